@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ray-bounces/s of the path-tracing hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 1..5] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config 1..5] [--scaling weak|strong] [--dump-outputs DIR]
 
 `--config` picks one of BASELINE.json's configurations (scene, resolution, depth; default 2 = the headline one);
 `--steps` defaults to the config's spp.  `--scaling strong` keeps the config's frame fixed and cuts it into N tiles
@@ -23,7 +23,10 @@ inputs resident in HBM before the timed region.  The `roofline` block prices the
 against HBM: algorithmic bytes of the timed region's launches / the HIP-event time of the timed
 region on the render stream (two launch sequences are in flight, so a launch's own duration overlaps its
 neighbour's: the block also carries the kernel-alone figure from per-launch events).  `cpu_baseline` times the CPU
-oracle on a bounded sample of the same workload on this box's host cores (rank 0, N=1 only).
+oracle on a bounded sample of the same workload on this box's host cores (rank 0, N=1 only).  `ms_per_step` = wall time
+of the timed region / K.  The K timed steps are iterations 1..K of the frame, whatever the warm-up did, so with the same
+arguments they compute the same pixels in every run: `--dump-outputs DIR` writes them (and the per-bounce ray counts) as
+.npy files for comparing two builds output for output.
 """
 import argparse
 import ctypes as C
@@ -91,7 +94,12 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="PMC-derived HBM bytes per launch per config (written from profiles/collect_pmc.py summaries), if present")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed as DIR/<name>.npy (rank 0): the framebuffer of the last "
+                         "timed step (a seeded sample of its pixels when it exceeds 48 MB) and the ray counts per bounce")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
     args.custom = any(v is not None for v in (args.scene, args.width, args.height, args.depth, args.rotat))
     args.scene = args.scene or cfg["scene"]
@@ -145,6 +153,30 @@ def cpu_baseline(args, scene_path, rotat):
                       f"{'' if scale == 1 else f' (1/{scale} of the resolution)'} "
                       f"({rb} ray-bounces in {dt:.2f} s, oracle/pt_oracle.c, {cores} threads)",
             "ms_per_frame": dt / spp * 1e3 * scale * scale}
+
+
+DUMP_IMAGE_MAX_BYTES = 48 << 20     # larger framebuffers are dumped as a sample of pixels (with their indices): <= 64 MB in all
+DUMP_SAMPLE_PIXELS = 1 << 21
+
+
+def dump_outputs(out_dir, image, live_in):
+    """What the timed path computed in its last step: the framebuffer (running mean, float32 [H, W, 3]) and the ray counts
+    per bounce of the timed steps.  Same arguments -> same inputs -> same files, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes <= DUMP_IMAGE_MAX_BYTES:
+        files["image"] = img
+    else:
+        pix = img.reshape(-1, 3)
+        idx = np.sort(np.random.default_rng(0).choice(pix.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+        files["image_sample"] = pix[idx]
+        files["image_sample_pixels"] = idx.astype(np.float64)      # flat pixel index y * W + x
+    files["live_in_per_bounce"] = np.asarray(live_in, dtype=np.float64)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "files": {name + ".npy": list(arr.shape) for name, arr in files.items()}}
 
 
 def main():
@@ -290,21 +322,14 @@ def main():
         r.synchronize()
         chunk_s.append(time.perf_counter() - t_c)
         settle_iters += chunk
-    if world > 1:
-        # every rank leaves the settle phase at its own iteration count (it only has to be warm); agree on the largest so
-        # that the timed iterations carry the same numbers everywhere (RNG streams are keyed on them)
-        tmp = torch.tensor([float(settle_iters)], dtype=torch.float64, device="cpu" if rehearsal else dev)
-        dist.all_reduce(tmp, op=dist.ReduceOp.MAX)
-        more = int(tmp[0]) - settle_iters
-        if more > 0:
-            r.render(next_iter + settle_iters, more)
-            settle_iters += more
     sync()
     r.reset_stats()
 
     # timed region: exactly K steps, then (N > 1) the ONE framebuffer gather of the frame those steps rendered -- the
-    # path's only exchange step, dependent on the render, inside the barriers.
-    first = next_iter + settle_iters
+    # path's only exchange step, dependent on the render, inside the barriers.  The steps are iterations 1..K: iteration 1
+    # restarts the running mean (k_accumulate), so the region renders a fresh K-spp frame whose pixels do not depend on how
+    # many untimed iterations the settle phase took (RNG streams are keyed on the iteration numbers).
+    first = 1
     sync()
     t0 = time.perf_counter()
     r.render(first, args.steps)
@@ -313,6 +338,9 @@ def main():
         frame = gather(fb)
     sync()
     dt = time.perf_counter() - t0
+    dumped_image = None
+    if args.dump_outputs and rank == 0:     # before anything renders into the framebuffer again
+        dumped_image = (frame if world > 1 else fb[:Hband]).cpu().numpy().copy()
 
     st = r.stats()
     rb_local = int(st.ray_bounces)
@@ -519,6 +547,8 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, scene_path, rotat)
             out["vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, dumped_image, live_in)
         print(json.dumps(out), flush=True)
 
     r.close()

@@ -1,7 +1,7 @@
 # Round evidence on ONE box: bench lines of every BASELINE config + variants, rocprofv3 kernel traces (two sequences in flight and
 # one), PMC passes.   gpurun -- 'bash profiles/evidence.sh r03final'   ->  gpurun_out/<tag>/ ; copy what is cited into profiles/r03/
 T=${1:-r03final}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p gpurun_out/$T && cd gpurun_out/$T
 python $R/bench.py > bench_config2.json 2> c2.err
 python $R/bench.py --steps 20 --warmup 5 > bench_driver_cmd_20_5.json 2>> c2.err

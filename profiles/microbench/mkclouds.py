@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "scenes"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "scenes"))
 import make_scenes as ms
 ms.HERE = sys.argv[1]
 for n in (24, 32, 48, 64, 96, 128):
