@@ -1,7 +1,7 @@
 #!/bin/bash
 # build_variant.sh NAME "UNITS" "EXTRA FLAGS": rebuild some translation units with extra flags and link a library of its own beside the
 # product one (project3-pathtracer_amd/lib_NAME/libptamd.so; select it with PT_LIBPTAMD=...).  UNITS: bounce unit numbers 0..7 and / or
-# kernels, context, multi.  The other objects come from the product build (make -C csrc first).
+# kernels, context, tables, multi.  The other objects come from the product build (make -C csrc first).
 set -e
 NAME=$1; UNITS=$2; EXTRA=$3
 cd "$(dirname "$0")/../project3-pathtracer_amd/csrc"
@@ -13,6 +13,7 @@ for u in $UNITS; do
     [0-7]) f=pt_bounce_g$u ;;
     kernels) f=pt_kernels ;;
     context) f=pt_context ;;
+    tables) f=pt_tables ;;
     multi) f=pt_multi ;;
     *) echo "unknown unit $u"; exit 2 ;;
   esac
