@@ -29,7 +29,6 @@ static constexpr bool DEBUG_SPAN = PT_DEBUG_SPAN != 0;       // workgroup lifeti
 #define PT_DEBUG_BOUNDS 0
 #endif
 static constexpr bool DEBUG_BOUNDS = PT_DEBUG_BOUNDS != 0;   // index checks before global accesses; first violation -> IterState::dbg
-static constexpr bool DEBUG_CULL = false;
 static constexpr bool DEBUG_PAIR = PT_DEBUG_PAIR != 0;
 static constexpr bool DEBUG_PHASE = PT_DEBUG_PHASE == 1;     // per-wave shader-clock stamps between the phases of a chunk -> IterState::dbg
 static constexpr bool DEBUG_PHASE2 = PT_DEBUG_PHASE == 2;    // finer split of the later bounces (pair-queue path): load, pre-test loop
@@ -203,11 +202,7 @@ __device__ __forceinline__ Hit nearestHitDirect(const KParams &p, const PR *s_pr
             mat = P.material;
         } else {
             const Prim P = load_prim_scalar(p.prims, g);
-            if (p.cull) {
-                const bool skip = waveMissesBound(P, o, d);
-                if (DEBUG_CULL && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0) atomicAdd(&p.st->clk[skip ? 3 : 2], 1ull);
-                if (skip) continue;
-            }
+            if (p.cull && waveMissesBound(P, o, d)) continue;
             t = intersectPrim<FIRST>(P, o, d, FIRST ? load_ro_eye(p.ro_eye, g) : o, ip, in);
             mat = P.material;
         }
@@ -987,6 +982,31 @@ static constexpr uint32_t W4_STACK = 512;                              // traver
 // more for their address arithmetic): three 512-thread workgroups per CU beside a 13 KB node copy instead of two.
 static constexpr uint32_t W4_PAIR_BYTES = 2 * QCAP * 4 + 64 * 8 + 64 * 16;
 __host__ __device__ constexpr uint32_t walk4_wave_bytes(int ntri) { return W4_PAIR_BYTES + W4_STACK * 4 + (ntri > 0 ? QCAP * 4 : 0); }
+// k_bounce's dynamic LDS, region by region in the order k_bounce carves it (I = int); the host sizes the launch by the total (I = size_t).
+//   [prims + face normals] [nodes / boxes] [per-wave queues] [material planes] [scan scratch] [resident: stream keys, histogram]
+template <class I> struct BounceLds {
+    I prim_bytes, node_bytes, wave_bytes, total;       // bytes: records + face normals, nodes or boxes, one wave's queues; all
+    I mat_words, scan_words, key_words, term_words;    // 32-bit words
+};
+template <class I>
+__host__ __device__ __forceinline__ BounceLds<I> bounce_lds(const KParams &p, int geom, int nw, bool nee, bool motion, bool resident)
+{
+    BounceLds<I> l;
+    l.prim_bytes = (geom == GEOM_LDS || geom == GEOM_QUEUE || geom == GEOM_PAIR) ? (I)p.nG * (I)(2 * sizeof(PrimPad)) : 0;   // records, then 8 face normals each (padded alike)
+    // pair queue: the node region holds the primitives' padded boxes (relative to the eye for camera rays; NEE: world boxes behind)
+    l.node_bytes = (geom == GEOM_BVH || geom == GEOM_WALK_PAIR) ? (I)p.nnodes * (I)sizeof(BvhNode)
+                   : geom == GEOM_WALK4 ? (((I)p.nnodes4 * W4_FLOATS * 4 + 127) & ~(I)127)
+                   : geom == GEOM_PAIR ? (I)p.nG * PAIR_BOX_BYTES * (nee ? 2 : 1) : 0;
+    l.wave_bytes = geom == GEOM_QUEUE ? (I)WAVE_QUEUE_BYTES
+                   : (geom == GEOM_PAIR || geom == GEOM_WALK_PAIR) ? (I)((motion && geom == GEOM_PAIR) ? PAIR_QUEUE_MOTION_BYTES : PAIR_QUEUE_BYTES)
+                   : (geom == GEOM_WALK4 || geom == GEOM_WALK4G) ? (I)walk4_wave_bytes(p.ntri) : 0;
+    l.mat_words = (I)((p.nM * M_PLANES + 3) & ~3);
+    l.scan_words = (I)((2 * nw + 2 + 3) & ~3);
+    l.key_words = resident ? (I)(p.depth * MAXSLOT) : 0;
+    l.term_words = resident ? (I)((p.depth + 3) & ~3) : 0;
+    l.total = l.prim_bytes + l.node_bytes + (I)nw * l.wave_bytes + (l.mat_words + l.scan_words + l.key_words + l.term_words) * (I)sizeof(uint32_t);
+    return l;
+}
 struct Walk4 {
     const unsigned char *nodes;   // LDS copy of the 4-wide hierarchy (ptd::W4_FLOATS floats per node)
     uint32_t *stack;              // [W4_STACK] owner lane | direction signs << 6 | child word (bit 31 leaf, bit 30 cube, bit 29 triangle, bits 9..28 index)
@@ -1304,32 +1324,23 @@ __global__ __launch_bounds__(WG, ((FEAT & ~FEAT_SLAB) == FEAT_RESIDENT && (GEOM 
     constexpr int NW = WG / 64;
     constexpr bool PRIMS_IN_LDS = (GEOM == GEOM_LDS || GEOM == GEOM_QUEUE || GEOM == GEOM_PAIR);   // GEOM_BVH gathers records from global memory (L1/L2)
     extern __shared__ __attribute__((aligned(128))) unsigned char smem[];
-    // LDS carve: [prims nG*128 B (GEOM 1,2)] [per-wave hit queues (GEOM 2)] [material planes] [scan scratch]
+    // LDS carve: the regions of bounce_lds(), whose total sizes the launch
+    const BounceLds<int> lds = bounce_lds<int>(p, GEOM, NW, NEE, MOTION, RESIDENT);
     PrimPad *s_prims = reinterpret_cast<PrimPad *>(smem);
-    const int prim_bytes = PRIMS_IN_LDS ? p.nG * (int)(2 * sizeof(PrimPad)) : 0;     // records, then 8 face normals each (padded alike)
-    const float4 *s_nodes = reinterpret_cast<const float4 *>(smem + prim_bytes);
-    // pair queue: the same region holds the primitives' padded boxes (2 float4 each; relative to the eye for camera rays)
-    const int node_bytes = (GEOM == GEOM_BVH || GEOM == GEOM_WALK_PAIR) ? p.nnodes * (int)sizeof(BvhNode)
-                           : (GEOM == GEOM_WALK4 ? ((p.nnodes4 * W4_FLOATS * 4 + 127) & ~127)
-                                                 : (GEOM == GEOM_PAIR ? p.nG * PAIR_BOX_BYTES * (NEE ? 2 : 1) : 0));
-    unsigned char *s_queue = smem + prim_bytes + node_bytes;
-    const int WAVE_LDS = (GEOM == GEOM_QUEUE) ? (int)WAVE_QUEUE_BYTES
-                         : ((GEOM == GEOM_PAIR || GEOM == GEOM_WALK_PAIR) ? (int)((MOTION && GEOM == GEOM_PAIR) ? PAIR_QUEUE_MOTION_BYTES : PAIR_QUEUE_BYTES)
-                            : ((GEOM == GEOM_WALK4 || GEOM == GEOM_WALK4G) ? (int)walk4_wave_bytes(p.ntri) : 0));
-    const int queue_bytes = NW * WAVE_LDS;
-    float *s_mats = reinterpret_cast<float *>(s_queue + queue_bytes);
-    const int mat_words = (p.nM * M_PLANES + 3) & ~3;
-    uint32_t *s_scan = reinterpret_cast<uint32_t *>(s_mats + mat_words);   // [2][NW] wave totals, [2] bases
+    const float4 *s_nodes = reinterpret_cast<const float4 *>(smem + lds.prim_bytes);
+    unsigned char *s_queue = smem + lds.prim_bytes + lds.node_bytes;
+    float *s_mats = reinterpret_cast<float *>(s_queue + NW * lds.wave_bytes);
+    uint32_t *s_scan = reinterpret_cast<uint32_t *>(s_mats + lds.mat_words);   // [2][NW] wave totals, [2] bases
     // RESIDENT: stream keys of every (bounce, iteration slot) and the histogram of the bounce each path ended at
-    uint32_t *s_keys = s_scan + ((2 * NW + 2 + 3) & ~3);                   // [depth][MAXSLOT]
-    uint32_t *s_term = s_keys + (RESIDENT ? p.depth * MAXSLOT : 0);        // [depth]
+    uint32_t *s_keys = s_scan + lds.scan_words;                            // [depth][MAXSLOT]
+    uint32_t *s_term = s_keys + lds.key_words;                             // [depth]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: chunk bookkeeping runs on the scalar unit
 
     WaveQueue wq;
     {
-        unsigned char *b = s_queue + wave * WAVE_LDS;
+        unsigned char *b = s_queue + wave * lds.wave_bytes;
         wq.rec = reinterpret_cast<float4 *>(b);
         wq.key = reinterpret_cast<unsigned long long *>(b + QCAP * 32);
         wq.best = reinterpret_cast<float4 *>(b + QCAP * 32 + 64 * 8);
@@ -1349,7 +1360,7 @@ __global__ __launch_bounds__(WG, ((FEAT & ~FEAT_SLAB) == FEAT_RESIDENT && (GEOM 
     if (GEOM == GEOM_PAIR) {
         // (FEAT_MOTION: box_world holds the boxes swept over the shutter interval, and camera rays have no common eye)
         const uint4 *src = reinterpret_cast<const uint4 *>((FIRST && !MOTION && !(p.lens_radius > 0.0f)) ? p.box_eye : p.box_world);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem + prim_bytes);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem + lds.prim_bytes);
         // per primitive eight entries (near.xyz, 0)(far.xyz, -), one per direction octant (bit 0 / 1 / 2 = the ray runs towards -x / -y / -z)
         auto stage_oct = [&](const uint4 *from, uint4 *to) {
             for (int k = tid; k < p.nG * 8; k += WG) {
@@ -1364,12 +1375,12 @@ __global__ __launch_bounds__(WG, ((FEAT & ~FEAT_SLAB) == FEAT_RESIDENT && (GEOM 
     }
     if (GEOM == GEOM_BVH || GEOM == GEOM_WALK_PAIR) {
         const uint4 *src = reinterpret_cast<const uint4 *>(p.bvh);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem + prim_bytes);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem + lds.prim_bytes);
         for (int k = tid; k < p.nnodes * 2; k += WG) dst[k] = src[k];
     }
     if (GEOM == GEOM_WALK4) {
         const uint4 *src = reinterpret_cast<const uint4 *>(p.bvh4);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem + prim_bytes);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem + lds.prim_bytes);
         for (int k = tid; k < p.nnodes4 * (W4_FLOATS / 4); k += WG) dst[k] = src[k];
     }
     for (int k = tid; k < p.nM * M_PLANES; k += WG) s_mats[k] = p.mats[k];

@@ -258,19 +258,8 @@ __global__ __launch_bounds__(256) void k_send_image_to_pbo(pt_uchar4 *pbo, const
 // ---------------------------------------------------------------------------------------------
 size_t bounce_lds_bytes(const KParams &p, const LaunchCfg &cfg)
 {
-    size_t prim = (cfg.geom == GEOM_LDS || cfg.geom == GEOM_QUEUE || cfg.geom == GEOM_PAIR) ? (size_t)p.nG * 2 * sizeof(PrimPad) : 0;
-    size_t queue = (size_t)(cfg.workgroup / 64) * (cfg.geom == GEOM_QUEUE ? WAVE_QUEUE_BYTES
-                                                   : ((cfg.geom == GEOM_PAIR || cfg.geom == GEOM_WALK_PAIR) ? ((cfg.motion && cfg.geom == GEOM_PAIR) ? PAIR_QUEUE_MOTION_BYTES : PAIR_QUEUE_BYTES)
-                                                      : ((cfg.geom == GEOM_WALK4 || cfg.geom == GEOM_WALK4G) ? walk4_wave_bytes(p.ntri) : 0)));
-    if (cfg.geom == GEOM_WALK4) prim += ((size_t)p.nnodes4 * W4_FLOATS * 4 + 127) & ~(size_t)127;
-    if (cfg.geom == GEOM_BVH || cfg.geom == GEOM_WALK_PAIR) prim += (size_t)p.nnodes * sizeof(BvhNode);
-    if (cfg.geom == GEOM_PAIR) prim += (size_t)p.nG * PAIR_BOX_BYTES * (cfg.nee ? 2 : 1);
-    size_t mats = (size_t)((p.nM * M_PLANES + 3) & ~3) * sizeof(float);
-    size_t scan = (size_t)((2 * (cfg.workgroup / 64) + 2 + 3) & ~3) * sizeof(uint32_t);
     static const size_t extra = getenv("PT_EXTRA_LDS") ? (size_t)atol(getenv("PT_EXTRA_LDS")) : 0;   // occupancy experiments
-    // resident paths: stream keys of every (bounce, slot) and the histogram of the bounces the paths ended at
-    const size_t resident = cfg.resident ? (size_t)(p.depth * MAXSLOT + ((p.depth + 3) & ~3)) * sizeof(uint32_t) : 0;
-    return prim + queue + mats + scan + resident + extra;
+    return bounce_lds<size_t>(p, cfg.geom, cfg.workgroup / 64, cfg.nee != 0, cfg.motion != 0, cfg.resident != 0).total + extra;
 }
 
 // one translation unit per geometry path (pt_bounce_g<N>.hip)
